@@ -15,21 +15,34 @@ over xGMI (grouped ncclSend/ncclRecv) is timed separately, after the timed
 steps ("reassembly_to_rank0").  value = input bytes of all ranks / time (GB/s).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3-1024|c3-16384|c4]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \\
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
 ``--gpus N`` without a launcher starts the N rank processes itself (before any
 GPU call) and exits with the worst exit code.
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(headline, step percentiles and the roofline of the timed steps' own kernel
+times).  ``--full`` adds every other leg after the timed steps: the bit-exact
+round trip and decode figures, the reassembly onto rank 0, T_e2e, T_api, the
+other method sets, the multi-size walks, the like_reference walks and the CPU
+baselines (each still under its own switch: --no-verify, --no-e2e,
+--alt-methods, --walk-bytes, --ref-walk-bytes, --ref-full-walk-bytes,
+--api-bytes, --no-cpu-baseline).  ``--dump-outputs DIR`` writes what the last
+timed step handed its caller as DIR/<name>.npy (dump_outputs below).
 """
 import argparse
 import ctypes as C
 import glob
 import json
 import os
+import random
 import socket
 import subprocess
 import sys
 import time
+import zlib
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [REPO, os.path.join(REPO, "adaptive-compression_amd")]
@@ -61,6 +74,13 @@ def parse():
     ap.add_argument("--mode", default="native", choices=["native", "reference"])
     ap.add_argument("--methods", default="1,3,4,9")
     ap.add_argument("--seed", type=int, default=20250418)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg (round-trip check, decode, "
+                         "reassembly, e2e, api, other method sets, walks, CPU baselines); the switches "
+                         "below shape those legs and mean nothing without it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (body length, per-MiB CRC-32, a seeded sample "
+                         "of body blocks, statistics) as DIR/<name>.npy")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
@@ -91,6 +111,8 @@ def parse():
     ap.add_argument("--api-bytes", type=int, default=256 << 20,
                     help="input size of the AdaptiveCompressor.compress(path, path) leg (0: skip)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.config:
         a.size, a.chunk = CONFIGS[a.config]
     return a
@@ -447,6 +469,63 @@ def percentile(xs, q):
     return v[lo] + (v[hi] - v[lo]) * (k - lo)
 
 
+DUMP_BLOCK = 4096         # bytes per sampled body block
+DUMP_BLOCKS = 2048        # sampled blocks: 8 MiB of body bytes, 32 MiB as float32
+DUMP_CRC_SPAN = 1 << 20   # one CRC-32 per MiB of the body
+DUMP_SLAB = 64 << 20      # device-to-host copy granule (a multiple of both)
+
+
+def dump_outputs(dirname, prefix, d_out, body_len, st, seed):
+    """--dump-outputs: what the last timed step handed its caller -- the body
+    (out, out_len) and the statistics -- as float32 / float64 .npy files, every
+    value exact (bytes < 2^8, CRC-32 < 2^32, counts < 2^53):
+
+      body_len             [1]       f64  out_len
+      body_crc32           [ceil(out_len / 1 MiB)] f64  zlib.crc32 of each MiB of the body (all of it)
+      body_sample_offsets  [k]       f64  byte offsets of the sampled 4 KiB blocks
+      body_sample          [k, 4096] f32  their bytes (zero-padded past out_len); every block of a
+                                          body of up to 2048 blocks, else 2048 blocks drawn by
+                                          random.Random(seed) from the block count
+      method_usage         [256]     f64  ambc_stats.method_usage
+      stats                [6]       f64  total_chunks, compressed_chunks, raw_chunks, bytes_saved,
+                                          payload_bytes, overhead_bytes (the timing fields left out)
+
+    The input is a function of (--size, --seed) and the body of (input, --chunk,
+    --mode, --methods), so equal arguments give equal files on any build that
+    computes the same thing.  With --gpus N > 1 every rank writes its own shard's
+    body and the step's (all-reduced) statistics as rank<r>_<name>.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    nblk = -(-body_len // DUMP_BLOCK)
+    picks = list(range(nblk)) if nblk <= DUMP_BLOCKS else \
+        sorted(random.Random(seed).sample(range(nblk), DUMP_BLOCKS))
+    sample = np.zeros((len(picks), DUMP_BLOCK), dtype=np.float32)
+    crcs = []
+    slab = bytearray(min(DUMP_SLAB, max(body_len, 1)))
+    k = 0
+    for off in range(0, body_len, DUMP_SLAB):
+        m = min(DUMP_SLAB, body_len - off)
+        view = memoryview(slab)[:m]
+        d_out.download(m, off, out=view)
+        crcs.extend(zlib.crc32(view[o:o + DUMP_CRC_SPAN]) for o in range(0, m, DUMP_CRC_SPAN))
+        while k < len(picks) and picks[k] * DUMP_BLOCK < off + m:
+            blk = np.frombuffer(view, dtype=np.uint8, count=min(DUMP_BLOCK, off + m - picks[k] * DUMP_BLOCK),
+                                offset=picks[k] * DUMP_BLOCK - off)
+            sample[k, :len(blk)] = blk
+            k += 1
+    arrays = {
+        "body_len": np.array([body_len], dtype=np.float64),
+        "body_crc32": np.array(crcs, dtype=np.float64),
+        "body_sample_offsets": np.array(picks, dtype=np.float64) * DUMP_BLOCK,
+        "body_sample": sample,
+        "method_usage": np.array([st.method_usage[i] for i in range(256)], dtype=np.float64),
+        "stats": np.array([st.total_chunks, st.compressed_chunks, st.raw_chunks, st.bytes_saved,
+                           st.payload_bytes, st.overhead_bytes], dtype=np.float64),
+    }
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirname, f"{prefix}{name}.npy"), arr)
+
+
 def pmc_traffic(workload):
     """HBM bytes per k_encode launch from a committed rocprofv3 --pmc summary
     (scripts/pmc_summary.py), if one exists for this workload (newest round wins)."""
@@ -530,9 +609,12 @@ def main():
     body_total = body_len if world == 1 else info.total
     if world > 1:
         dt = max(x[0] for x in group.host.allgather_obj([dt]))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, f"rank{rank}_" if world > 1 else "", d_out, body_len, st, args.seed)
+    full = args.full    # every leg from here to the result line
 
     reasm = shard_check = None
-    if world > 1:
+    if full and world > 1:
         # the whole body onto rank 0 in file order (grouped send/recv over xGMI), outside the timed steps
         d_all = _lib.DeviceBuffer(ctx, (body_total if rank == 0 else 0) + 64)
         group.barrier()
@@ -559,7 +641,7 @@ def main():
             shard_check = all(x[0] == 1.0 for x in oks)
 
     verified = decode = None
-    if not args.no_verify and world == 1:
+    if full and not args.no_verify and world == 1:
         # bit-exact round trip of the last step's body (outside the timed region)
         body_host = bytes(d_out.download(body_len))
         from ambc import AdaptiveCompressor
@@ -587,10 +669,10 @@ def main():
 
     e2e = api = None
     alts = []
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if full and rank == 0 and world == 1 and not args.no_e2e:
         e2e = e2e_leg(lib, ctx, d_in.ptr, body_len, n, p, d_out.ptr)
         log(f"e2e: {e2e}")
-    if rank == 0 and world == 1 and args.alt_methods:
+    if full and rank == 0 and world == 1 and args.alt_methods:
         for ms in args.alt_methods.split(";"):
             if ms.strip():
                 z = ms.strip().endswith("z")   # "...z": id 5 as zlib-9's own bytes
@@ -599,21 +681,21 @@ def main():
                 log(f"alt: {alt}")
                 alts.append(alt)
     walks = []
-    if rank == 0 and world == 1 and args.walk_bytes:
+    if full and rank == 0 and world == 1 and args.walk_bytes:
         for ms in args.walk_methods.split(";"):
             if ms.strip():
                 w = walk_leg(ctx, args.walk_bytes, [int(x) for x in ms.split(",")])
                 log(f"walk: {w}")
                 walks.append(w)
     ref_walk = ref_full = None
-    if rank == 0 and world == 1 and args.ref_walk_bytes:
+    if full and rank == 0 and world == 1 and args.ref_walk_bytes:
         ref_walk = ref_walk_leg(ctx, args.ref_walk_bytes)
         log(f"like_reference walk: {ref_walk}")
-    if rank == 0 and world == 1 and args.ref_full_walk_bytes:
+    if full and rank == 0 and world == 1 and args.ref_full_walk_bytes:
         ref_full = ref_walk_leg(ctx, args.ref_full_walk_bytes, full_set=True,
                                 check_bytes=args.ref_full_walk_check_bytes)
         log(f"like_reference full walk: {ref_full}")
-    if rank == 0 and world == 1 and args.api_bytes:
+    if full and rank == 0 and world == 1 and args.api_bytes:
         api = api_leg(args.api_bytes, args.chunk, args.mode, methods, args.seed)
         log(f"api: {api}")
 
@@ -628,7 +710,7 @@ def main():
         pmc = pmc_traffic(workload)
         result = {
             "metric": METRIC, "value": round(value, 3), "unit": "GB/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup,
+            "steps": len(step_s), "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
             "config": {"workload": workload, "config": args.config or "c2",
@@ -652,7 +734,7 @@ def main():
                          "algorithmic_bytes_per_launch": round(algo_bytes),
                          "launches_per_step": launches[0]},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             threads = int(os.environ.get("OMP_NUM_THREADS", "0")) or (os.cpu_count() or 1)
             result["cpu_baseline"] = cpu_baseline(args, threads, methods)
             if ref_walk is not None and args.ref_walk_check_bytes:

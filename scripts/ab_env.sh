@@ -10,7 +10,7 @@ A=${ARGS:---no-e2e --no-verify --alt-methods 1,3,4,5z --steps 2 --warmup 1}
 for rep in $(seq 1 ${REPS:-2}); do
   for v in base knob; do
     if [ $v = knob ]; then export ${ENVKV}; else unset ${ENVKV%%=*}; fi
-    timeout -k 10 300 python3 bench.py --no-cpu-baseline --api-bytes 0 $A > $O/${v}_$rep.json 2> $O/${v}_$rep.err
+    timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --api-bytes 0 $A > $O/${v}_$rep.json 2> $O/${v}_$rep.err
     python3 -c "
 import json
 d=json.loads(open('$O/${v}_$rep.json').read().strip().splitlines()[-1]); c=d['config']

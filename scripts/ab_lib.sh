@@ -9,7 +9,7 @@ mkdir -p $O
 for rep in $(seq 1 ${REPS:-3}); do
   for v in base $EXP; do
     L=adaptive-compression_amd/ambc/libambc_hip.so; [ $v != base ] && L=adaptive-compression_amd/ambc/libambc_hip_$v.so
-    AMBC_LIB=$L timeout -k 10 300 python3 bench.py --no-cpu-baseline --api-bytes 0 --no-e2e --no-verify $ARGS > $O/${v}_$rep.json 2> $O/${v}_$rep.err
+    AMBC_LIB=$L timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --api-bytes 0 --no-e2e --no-verify $ARGS > $O/${v}_$rep.json 2> $O/${v}_$rep.err
     python3 -c "
 import json,sys
 d=json.loads(open('$O/${v}_$rep.json').read().strip().splitlines()[-1])

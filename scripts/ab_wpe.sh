@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=gpurun_out/wpe
 mkdir -p $O
 run() {  # tag lib chunk glmin
-  AMBC_LIB=$2 AMBC_ENC_GL_MIN=$4 timeout -k 10 200 python3 bench.py --chunk $3 --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods "" --walk-bytes 0 --steps 10 --warmup 3 > $O/$1.json 2> $O/$1.err
+  AMBC_LIB=$2 AMBC_ENC_GL_MIN=$4 timeout -k 10 200 python3 bench.py --full --chunk $3 --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods "" --walk-bytes 0 --steps 10 --warmup 3 > $O/$1.json 2> $O/$1.err
 }
 for r in 1 2; do
   run base_4k_$r ab/lib_base.so 4096 8192

@@ -6,7 +6,7 @@ O=gpurun_out/wpe2
 mkdir -p $O
 run() {  # tag lib chunk [env...]
   local t=$1 l=$2 c=$3; shift 3
-  env AMBC_LIB=$l "$@" timeout -k 10 200 python3 bench.py --chunk $c --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods "" --walk-bytes 0 --steps 10 --warmup 3 > $O/$t.json 2> $O/$t.err
+  env AMBC_LIB=$l "$@" timeout -k 10 200 python3 bench.py --full --chunk $c --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods "" --walk-bytes 0 --steps 10 --warmup 3 > $O/$t.json 2> $O/$t.err
 }
 for r in 1 2; do
   for c in 4096 1024 2048 8192 16384; do

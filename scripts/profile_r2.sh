@@ -10,15 +10,15 @@ set -e
 export TMPDIR=/tmp
 O=gpurun_out/r2
 mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods '' --no-verify --steps 2 --warmup 1"
+B="python3 bench.py --full --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods '' --no-verify --steps 2 --warmup 1"
 SQ1="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU"
 SQ2="SQ_INSTS_SMEM SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_BRANCH"
 run() {  # name, counters, command...
     local name=$1 ctr=$2; shift 2
     timeout -s KILL 150 rocprofv3 --pmc $ctr --output-format csv -d $O/$name -o run -- "$@" > $O/$name.log 2>&1
 }
-run fetch "FETCH_SIZE" python3 bench.py --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods "" --no-verify --steps 2 --warmup 1
-run write "WRITE_SIZE" python3 bench.py --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods "" --no-verify --steps 2 --warmup 1
+run fetch "FETCH_SIZE" python3 bench.py --full --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods "" --no-verify --steps 2 --warmup 1
+run write "WRITE_SIZE" python3 bench.py --full --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods "" --no-verify --steps 2 --warmup 1
 run sq_enc1 "$SQ1" python3 scripts/kbench.py --msets "1,3,4,9" --inputs random,ascii,mixed --reps 1
 run sq_enc2 "$SQ2" python3 scripts/kbench.py --msets "1,3,4,9" --inputs random,ascii,mixed --reps 1
 run sq_alt1 "$SQ1" python3 scripts/kbench.py --msets "1,3,4,5;1,2,3,4" --inputs ascii,mixed --reps 1

@@ -6,12 +6,12 @@ set -e
 export TMPDIR=/tmp
 O=gpurun_out/r4p
 mkdir -p $O
-timeout -k 10 500 python3 -u bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 500 python3 -u bench.py --full > $O/bench.json 2> $O/bench.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -o run -- \
-    python3 bench.py --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods 1,3,4 --walk-bytes 0 --ref-walk-bytes 0 --steps 5 --warmup 2 > $O/prof_stats.log 2>&1
+    python3 bench.py --full --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods 1,3,4 --walk-bytes 0 --ref-walk-bytes 0 --steps 5 --warmup 2 > $O/prof_stats.log 2>&1
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o run -- \
-    python3 bench.py --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods 1,3,4 --walk-bytes 0 --ref-walk-bytes 0 --no-verify --steps 2 --warmup 1 > $O/pmc_fetch.log 2>&1
+    python3 bench.py --full --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods 1,3,4 --walk-bytes 0 --ref-walk-bytes 0 --no-verify --steps 2 --warmup 1 > $O/pmc_fetch.log 2>&1
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o run -- \
-    python3 bench.py --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods 1,3,4 --walk-bytes 0 --ref-walk-bytes 0 --no-verify --steps 2 --warmup 1 > $O/pmc_write.log 2>&1
+    python3 bench.py --full --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods 1,3,4 --walk-bytes 0 --ref-walk-bytes 0 --no-verify --steps 2 --warmup 1 > $O/pmc_write.log 2>&1
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU --output-format csv -d $O/sq_enc1 -o run -- python3 scripts/kbench.py --msets "1,3,4,9" --inputs random,ascii,mixed --reps 1 > $O/sq_enc1.log 2>&1
 timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_SMEM SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_BRANCH --output-format csv -d $O/sq_enc2 -o run -- python3 scripts/kbench.py --msets "1,3,4,9" --inputs random,ascii,mixed --reps 1 > $O/sq_enc2.log 2>&1

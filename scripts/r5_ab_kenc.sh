@@ -15,4 +15,4 @@ for rep in 1 2 3; do
   done
 done
 timeout -k 10 300 python3 -u -m pytest tests/test_gpu_zlib9.py tests/test_gpu_parity.py -m gpu -x -q --timeout 120 --timeout-method thread > $O/tests.log 2>&1
-timeout -k 10 400 python3 -u bench.py --steps 10 --warmup 3 --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods "1,3,4;1,3,4,5z" --walk-bytes 0 --ref-full-walk-bytes 0 > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python3 -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods "1,3,4;1,3,4,5z" --walk-bytes 0 --ref-full-walk-bytes 0 > $O/bench.json 2> $O/bench.err

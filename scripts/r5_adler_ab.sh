@@ -11,7 +11,7 @@ echo tests new ok
 for rep in 1 2; do
   for lib in base new; do
     f=$L/libambc_hip.so; [ $lib = base ] && f=$L/libambc_hip_base.so
-    AMBC_LIB=$f timeout -k 10 400 python3 bench.py --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods "1,3,4,5;1,3,4,5z" --walk-bytes 0 --ref-walk-bytes 0 --ref-full-walk-bytes 0 --steps 3 --warmup 1 > $O/bench_${lib}_$rep.json 2> $O/bench_${lib}_$rep.err
+    AMBC_LIB=$f timeout -k 10 400 python3 bench.py --full --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods "1,3,4,5;1,3,4,5z" --walk-bytes 0 --ref-walk-bytes 0 --ref-full-walk-bytes 0 --steps 3 --warmup 1 > $O/bench_${lib}_$rep.json 2> $O/bench_${lib}_$rep.err
   done
 done
 echo ab ok

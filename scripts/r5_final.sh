@@ -7,10 +7,10 @@ set -e
 export TMPDIR=/tmp
 O=gpurun_out/${EV_OUT:-r5f}
 mkdir -p $O
-H="python3 bench.py --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods= --walk-bytes 0 --ref-walk-bytes 0 --ref-full-walk-bytes 0"
+H="python3 bench.py --full --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods= --walk-bytes 0 --ref-walk-bytes 0 --ref-full-walk-bytes 0"
 timeout -k 10 600 python3 -u -m pytest tests -m gpu -v --timeout 120 --timeout-method thread > $O/tests.log 2>&1
 echo tests ok
-timeout -k 10 600 python3 -u bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 600 python3 -u bench.py --full > $O/bench.json 2> $O/bench.err
 echo bench ok
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -o run -- $H --steps 5 --warmup 2 > $O/prof_stats.log 2>&1
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o run -- $H --no-verify --steps 2 --warmup 1 > $O/pmc_fetch.log 2>&1

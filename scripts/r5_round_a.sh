@@ -26,11 +26,11 @@ done
 for lib in nopairs pairs; do
   f=$L/libambc_hip.so; [ $lib = nopairs ] && f=$L/libambc_hip_exp.so
   AMBC_LIB=$f timeout -k 10 200 python3 -u scripts/kbench.py --chunk 65536 --size 134217728 --msets "5" --flags 2 --inputs random,ascii,mixed --reps 2 > $O/kbench_z9big_$lib.log 2>&1
-  AMBC_LIB=$f timeout -k 10 300 python3 -u bench.py --steps 1 --warmup 0 --no-cpu-baseline --api-bytes 0 --no-e2e --no-verify --alt-methods "" --walk-bytes 0 --ref-full-walk-bytes 0 > $O/refwalk_$lib.json 2> $O/refwalk_$lib.err
+  AMBC_LIB=$f timeout -k 10 300 python3 -u bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --api-bytes 0 --no-e2e --no-verify --alt-methods "" --walk-bytes 0 --ref-full-walk-bytes 0 > $O/refwalk_$lib.json 2> $O/refwalk_$lib.err
 done
 for br in 128 256 512; do
-  AMBC_MS_BREADTH=$br timeout -k 10 300 python3 -u bench.py --steps 1 --warmup 0 --no-cpu-baseline --api-bytes 0 --no-e2e --no-verify --alt-methods "" --walk-bytes 0 --ref-full-walk-bytes 0 > $O/refwalk_br$br.json 2> $O/refwalk_br$br.err
+  AMBC_MS_BREADTH=$br timeout -k 10 300 python3 -u bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --api-bytes 0 --no-e2e --no-verify --alt-methods "" --walk-bytes 0 --ref-full-walk-bytes 0 > $O/refwalk_br$br.json 2> $O/refwalk_br$br.err
 done
-timeout -k 10 400 python3 -u bench.py --steps 5 --warmup 2 --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods "1,3,4;1,3,4,5z" --walk-bytes 0 --ref-full-walk-bytes 0 > $O/bench.json 2> $O/bench.err
-AMBC_TRACE=1 timeout -k 10 300 python3 -u bench.py --no-cpu-baseline --api-bytes 0 --no-e2e --no-verify --size 268435456 --alt-methods "" --ref-full-walk-bytes 0 --steps 1 --warmup 1 > $O/walktrace.json 2> $O/walktrace.err
-timeout -k 10 300 python3 -u bench.py --steps 1 --warmup 0 --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods "" --walk-bytes 0 --ref-walk-bytes 0 --no-verify > $O/fullwalk.json 2> $O/fullwalk.err
+timeout -k 10 400 python3 -u bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods "1,3,4;1,3,4,5z" --walk-bytes 0 --ref-full-walk-bytes 0 > $O/bench.json 2> $O/bench.err
+AMBC_TRACE=1 timeout -k 10 300 python3 -u bench.py --full --no-cpu-baseline --api-bytes 0 --no-e2e --no-verify --size 268435456 --alt-methods "" --ref-full-walk-bytes 0 --steps 1 --warmup 1 > $O/walktrace.json 2> $O/walktrace.err
+timeout -k 10 300 python3 -u bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods "" --walk-bytes 0 --ref-walk-bytes 0 --no-verify > $O/fullwalk.json 2> $O/fullwalk.err

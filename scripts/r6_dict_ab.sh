@@ -4,7 +4,7 @@
 set -e
 O=gpurun_out/${EV_OUT:-r6dab2}
 mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --api-bytes 0 --no-e2e --walk-bytes 0 --ref-walk-bytes 0 --ref-full-walk-bytes 0 --steps 3 --warmup 1 --alt-methods 1,2,3,4 --no-verify"
+B="python3 bench.py --full --no-cpu-baseline --api-bytes 0 --no-e2e --walk-bytes 0 --ref-walk-bytes 0 --ref-full-walk-bytes 0 --steps 3 --warmup 1 --alt-methods 1,2,3,4 --no-verify"
 for r in 1 2; do
   timeout -k 10 300 $B > $O/base_$r.json 2> $O/base_$r.err
   AMBC_LIB=$PWD/adaptive-compression_amd/ambc/libambc_hip_exp.so timeout -k 10 300 $B > $O/exp_$r.json 2> $O/exp_$r.err

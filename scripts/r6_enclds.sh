@@ -5,7 +5,7 @@ set -e
 export TMPDIR=/tmp
 O=gpurun_out/${EV_OUT:-r6enclds}
 mkdir -p $O
-H="python3 bench.py --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods= --walk-bytes 0 --ref-walk-bytes 0 --ref-full-walk-bytes 0"
+H="python3 bench.py --full --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods= --walk-bytes 0 --ref-walk-bytes 0 --ref-full-walk-bytes 0"
 for r in 1 2; do
   timeout -k 10 200 $H --steps 10 --warmup 3 > $O/gl_$r.json 2> $O/gl_$r.err
   AMBC_ENC_LDS=1 timeout -k 10 200 $H --steps 10 --warmup 3 > $O/lds_$r.json 2> $O/lds_$r.err

@@ -7,12 +7,12 @@ set -e
 export TMPDIR=/tmp
 O=gpurun_out/${EV_OUT:-r6f}
 mkdir -p $O
-H="python3 bench.py --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods= --walk-bytes 0 --ref-walk-bytes 0 --ref-full-walk-bytes 0"
+H="python3 bench.py --full --no-cpu-baseline --api-bytes 0 --no-e2e --alt-methods= --walk-bytes 0 --ref-walk-bytes 0 --ref-full-walk-bytes 0"
 timeout -k 10 600 python3 -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread > $O/tests.log 2>&1
 echo tests ok
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1
 echo smoke ok
-timeout -k 10 600 python3 -u bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 600 python3 -u bench.py --full > $O/bench.json 2> $O/bench.err
 echo bench ok
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -o run -- $H --steps 5 --warmup 2 > $O/prof_stats.log 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_dec -o run -- python3 scripts/decode_leg.py 2 > $O/prof_dec.log 2>&1

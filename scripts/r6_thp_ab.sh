@@ -7,7 +7,7 @@ O=gpurun_out/${EV_OUT:-r6thp}
 mkdir -p $O
 { cat /sys/kernel/mm/transparent_hugepage/enabled /sys/kernel/mm/transparent_hugepage/defrag \
       /sys/kernel/mm/transparent_hugepage/khugepaged/defrag 2>&1; grep -E "MemTotal|MemFree|MemAvailable|AnonHugePages|HugePages_|Hugepagesize" /proc/meminfo; nproc; } > $O/sys.txt 2>&1 || true
-B="python3 -u bench.py --no-cpu-baseline --api-bytes 0 --no-e2e --walk-bytes 0 --ref-walk-bytes 0 --ref-full-walk-bytes 0 --steps 2 --warmup 1 --alt-methods 1,3,4;1,3,4,5;1,2,3,4"
+B="python3 -u bench.py --full --no-cpu-baseline --api-bytes 0 --no-e2e --walk-bytes 0 --ref-walk-bytes 0 --ref-full-walk-bytes 0 --steps 2 --warmup 1 --alt-methods 1,3,4;1,3,4,5;1,2,3,4"
 for r in 1 2; do
   timeout -k 10 300 $B > $O/base_$r.json 2> $O/base_$r.err
   AMBC_NO_HUGEPAGE=1 timeout -k 10 300 $B > $O/nohp_$r.json 2> $O/nohp_$r.err

@@ -6,7 +6,7 @@ set -e
 O=gpurun_out/${EV_OUT:-r6z9abn}
 mkdir -p $O
 L=$PWD/adaptive-compression_amd/ambc
-B="python3 bench.py --no-cpu-baseline --api-bytes 0 --no-e2e --walk-bytes 0 --ref-full-walk-bytes 0 --ref-walk-check-bytes 0 --steps 2 --warmup 1 --alt-methods 1,3,4,5z --no-verify"
+B="python3 bench.py --full --no-cpu-baseline --api-bytes 0 --no-e2e --walk-bytes 0 --ref-full-walk-bytes 0 --ref-walk-check-bytes 0 --steps 2 --warmup 1 --alt-methods 1,3,4,5z --no-verify"
 for r in 1 2; do
   timeout -k 10 300 $B > $O/base_$r.json 2> $O/base_$r.err
   for x in $XS; do

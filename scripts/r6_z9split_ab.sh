@@ -5,7 +5,7 @@
 set -e
 O=gpurun_out/${EV_OUT:-r6z9split}
 mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --api-bytes 0 --no-e2e --walk-bytes 0 --ref-full-walk-bytes 0 --ref-walk-check-bytes 0 --steps 2 --warmup 1 --alt-methods 1,3,4,5z --ref-walk-bytes 0"
+B="python3 bench.py --full --no-cpu-baseline --api-bytes 0 --no-e2e --walk-bytes 0 --ref-full-walk-bytes 0 --ref-walk-check-bytes 0 --steps 2 --warmup 1 --alt-methods 1,3,4,5z --ref-walk-bytes 0"
 for r in 1 2; do
   AMBC_Z9_ONESTREAM=1 timeout -k 10 300 $B > $O/base_$r.json 2> $O/base_$r.err
   timeout -k 10 300 $B > $O/exp_$r.json 2> $O/exp_$r.err

@@ -299,7 +299,7 @@ def test_two_rank_rccl_bench(hip_lib):
     s.bind(("127.0.0.1", 0))
     s.close()
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2",
-                        "--warmup", "1", "--size", str(256 << 20), "--no-cpu-baseline"],
+                        "--warmup", "1", "--size", str(256 << 20), "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     import json
