@@ -32,7 +32,9 @@ MODE_REFERENCE = 1
 FLAG_NO_END_CHUNK = 1
 FLAG_ZLIB9 = 2          # id 5 = zlib.compress(data, 9)'s bytes (chunk_size <= 65536)
 FLAG_INPUT_PADDED = 4   # device inputs: 64 readable bytes after n (large chunks read in place)
+FLAG_LZ4HC = 8          # id 9 = "ambc-lz4 hc v1" (chunk_size <= 16384; not in the multi-size walk)
 MAX_CHUNK = 65536
+LZ4HC_MAX_CHUNK = 16384
 
 EXPORTS = (
     "ambc_abi_version", "ambc_last_error", "ambc_device_count", "ambc_init", "ambc_destroy",
@@ -47,7 +49,7 @@ EXPORTS = (
     "ambc_compress_shard", "ambc_decompress_shard", "ambc_decompress_multi",
     "ambc_synth_device_range", "ambc_device_equal", "ambc_compress_multisize",
     "ambc_last_multisize_info", "ambc_fetch_body", "ambc_compress_multisize_ex", "ambc_debug_walk",
-    "ambc_test_inject_failure",
+    "ambc_test_inject_failure", "ambc_encode_method_ex", "ambc_lz4hc_model", "ambc_lz4hc_model_ex",
 )
 
 
@@ -109,6 +111,9 @@ def _declare(lib):
         "ambc_compress_device": ([vp, i32, vp, u64, C.POINTER(Params), vp, u64, C.POINTER(u64),
                                   C.POINTER(Stats), vp], i32),
         "ambc_encode_method": ([vp, i32, u8p, u32, u8p, u32, C.POINTER(u32)], i32),
+        "ambc_encode_method_ex": ([vp, i32, u32, u8p, u32, u8p, u32, C.POINTER(u32)], i32),
+        "ambc_lz4hc_model": ([u8p, u32, u8p, u32, C.POINTER(u32)], i32),
+        "ambc_lz4hc_model_ex": ([u8p, u32, u32, u32, u8p, u32, C.POINTER(u32)], i32),
         "ambc_analyze": ([vp, u8p, u64, C.POINTER(Params), u8p, u8p, u8p], i32),
         "ambc_dict_encode": ([vp, u8p, u64, C.c_int64, C.c_int64, u8p, u64, C.POINTER(u64)], i32),
         "ambc_encode_any": ([vp, i32, u8p, u64, u8p, u64, C.POINTER(u64)], i32),

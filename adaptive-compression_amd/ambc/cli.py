@@ -35,7 +35,8 @@ def get_method_name(method_id):
 def _compressor(args):
     from .compressor import AdaptiveCompressor
     methods = tuple(int(x) for x in args.methods.split(",")) if args.methods else None
-    comp = AdaptiveCompressor(chunk_size=args.chunk_size, mode=args.mode, methods=methods)
+    comp = AdaptiveCompressor(chunk_size=args.chunk_size, mode=args.mode, methods=methods,
+                              lz4=getattr(args, "lz4", None))
     if args.reference_candidates:
         comp.CHUNK_SIZE_CANDIDATES = list(REFERENCE_CHUNK_SIZE_CANDIDATES)
     return comp
@@ -118,6 +119,8 @@ def build_parser():
     c.add_argument("--chunk-size", type=int, default=None, help="CHUNK_SIZE_CANDIDATES=[C] (default 4096)")
     c.add_argument("--mode", choices=["native", "reference"], default="native")
     c.add_argument("--methods", default=None, help="GPU method ids, e.g. 1,3,4,9 (default) or 1,2,3,4")
+    c.add_argument("--lz4", choices=["greedy", "hc"], default=None,
+                   help="id 9's encoder: greedy (default) or hc (hash chains + lazy parse; chunk size <= 16384)")
     c.add_argument("--reference-candidates", action="store_true",
                    help="the reference's 8-size CHUNK_SIZE_CANDIDATES walk (adaptive_compressor.py:61-62)")
     c.add_argument("--history", default=HISTORY, help="history JSON ('' to skip)")

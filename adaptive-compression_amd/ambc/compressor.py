@@ -89,7 +89,7 @@ class AdaptiveCompressor:
     REFERENCE_CHUNK_SIZE_CANDIDATES = list(REFERENCE_CHUNK_SIZE_CANDIDATES)
 
     def __init__(self, marker_max_length=32, sample_size=10000, *, chunk_size=None,
-                 mode="native", methods=None, devices=None, deflate=None):
+                 mode="native", methods=None, devices=None, deflate=None, lz4=None):
         self.marker_max_length = marker_max_length
         self.sample_size = sample_size
         self.marker_finder = None          # the reference's finder is never called (:303-310)
@@ -112,6 +112,12 @@ class AdaptiveCompressor:
         if deflate not in (None, "v1", "zlib9"):
             raise ValueError("deflate must be None, 'v1' or 'zlib9'")
         self._deflate = deflate
+        # id 9's GPU encoder: "greedy" ("ambc-lz4 greedy v2", the default) or "hc"
+        # ("ambc-lz4 hc v1": hash chains and a lazy parse -- smaller frames, slower;
+        # chunk_size <= 16384, one chunk size).  Both write valid LZ4 frames.
+        if lz4 not in (None, "greedy", "hc"):
+            raise ValueError("lz4 must be None, 'greedy' or 'hc'")
+        self.lz4 = lz4 or "greedy"
         # encode defaults left as they are: the first compress says they are not the reference's
         self._warn_defaults = chunk_size is None and mode == "native" and methods is None
         if chunk_size is not None:
@@ -212,6 +218,10 @@ class AdaptiveCompressor:
         p.mode = _lib.MODE_REFERENCE if self.mode == "reference" else _lib.MODE_NATIVE
         p.flags = _lib.FLAG_ZLIB9 if self.deflate == "zlib9" else 0
         p.method_mask = method_mask(self._gpu_ids())
+        if self.lz4 == "hc" and 9 in self._gpu_ids():
+            if C_ > _lib.LZ4HC_MAX_CHUNK:
+                raise ValueError(f"lz4='hc' takes chunk_size <= {_lib.LZ4HC_MAX_CHUNK} (got {C_})")
+            p.flags |= _lib.FLAG_LZ4HC
         for i in range(16):
             lo, hi = self.method_chunk_prefs.get(i, (1, 0))
             p.pref_min[i], p.pref_max[i] = max(0, lo), min(hi, 0xFFFFFFFF)
@@ -241,6 +251,9 @@ class AdaptiveCompressor:
         winner -> the remainder raw) as many lock-step walks over the device-
         resident input, one batched encode per size and step."""
         n = len(file_data)
+        if self.lz4 == "hc" and 9 in self._gpu_ids():
+            raise ValueError("lz4='hc' is not available in the multi-size walk "
+                             "(several CHUNK_SIZE_CANDIDATES, or host-scored ids 6 / 7)")
         ctx = self._ctx()
         cands = [int(c) for c in self.CHUNK_SIZE_CANDIDATES]
         p = _lib.Params()

@@ -107,6 +107,25 @@ def _gpu_encode(mid, data):
     return C.string_at(C.addressof(out), olen.value)
 
 
+def _gpu_encode_lz4hc(data):
+    """LZ4Compression(level="hc").compress: one chunk's "ambc-lz4 hc v1" frame."""
+    data = bytes(data)
+    n = len(data)
+    if n == 0:
+        return b""
+    if n > _lib.LZ4HC_MAX_CHUNK:
+        raise ValueError(f"LZ4Compression(level='hc') takes at most {_lib.LZ4HC_MAX_CHUNK} bytes (got {n})")
+    ctx = _ctx()
+    cap = n + 64
+    out = (C.c_uint8 * cap)()
+    olen = C.c_uint32()
+    with ctx.lock:
+        rc = ctx.lib.ambc_encode_method_ex(ctx.h, 9, _lib.FLAG_LZ4HC, _lib.addr(data), n, C.addressof(out), cap,
+                                           C.byref(olen))
+    _lib.check(rc, ctx.lib)
+    return C.string_at(C.addressof(out), olen.value)
+
+
 def _gpu_should_use(data):
     """should_use bits from the selector kernels: {1: RLE, 2: Dictionary, 3: Huffman, 4: Delta}."""
     data = bytes(data)
@@ -287,10 +306,19 @@ class DeltaCompression(CompressionMethod):
 
 class LZ4Compression(CompressionMethod):
     """advanced_compression.py:266-307 -- LZ4 frame from the gfx950 encoder
-    ("ambc-lz4 greedy v2" block parse, LZ4F one-block frame layout)."""
+    ("ambc-lz4 greedy v2" block parse, LZ4F one-block frame layout).
+    level="hc": "ambc-lz4 hc v1" (hash chains, lazy parse) for inputs up to 16384
+    bytes; longer inputs raise ValueError (the any-length path is greedy only)."""
     type_id = 9
 
+    def __init__(self, level="greedy"):
+        if level not in ("greedy", "hc"):
+            raise ValueError("level must be 'greedy' or 'hc'")
+        self.level = level
+
     def compress(self, data):
+        if self.level == "hc":
+            return _gpu_encode_lz4hc(data)
         return _gpu_encode(9, data)
 
     def decompress(self, data, original_length):

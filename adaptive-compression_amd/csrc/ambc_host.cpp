@@ -171,6 +171,8 @@ int ambc::check_params(const ambc_params* p) {
         return fail(AMBC_E_INVAL, "method_mask holds ids without a GPU encoder (allowed: 1, 2, 3, 4, 5, 9)");
     if (((p->method_mask >> AMBC_M_DEFLATE) & 1) && (p->flags & AMBC_FLAG_ZLIB9) && z9_cmax(C) == 0)
         return fail(AMBC_E_INVAL, "the GPU zlib-9 encoder (AMBC_FLAG_ZLIB9) supports chunk_size <= 65536");
+    if (((p->method_mask >> AMBC_M_LZ4) & 1) && (p->flags & AMBC_FLAG_LZ4HC) && C > LZ4HC_MAX_CHUNK)
+        return fail(AMBC_E_INVAL, "the GPU LZ4-HC encoder (AMBC_FLAG_LZ4HC) supports chunk_size <= 16384");
     if (((p->method_mask >> AMBC_M_DICT) & 1) && p->pref_min[AMBC_M_DICT] <= dict_cmax(p) &&
         dict_cmax(p) > 8192)
         return fail(AMBC_E_INVAL, "the GPU Dictionary encoder takes chunks <= 8192 bytes "
@@ -339,8 +341,11 @@ static int compress_on_body(Dev& d, const uint8_t* d_in, uint64_t n, const ambc_
     uint32_t gd_cmax = 1024;                  // launch_deflate's template bucket
     while (gd_cmax < C) gd_cmax <<= 1;
     const bool dict = (p->method_mask >> AMBC_M_DICT) & 1;
-    if (deflate || dict) {
-        // RLE / Huffman payloads wait for the later encoders' verdict (id 2, id 5);
+    // id 9 as "ambc-lz4 hc v1": k_encode runs without id 9, k_lz4hc after ids 2 / 5
+    const bool hc = ((p->method_mask >> AMBC_M_LZ4) & 1) && (p->flags & AMBC_FLAG_LZ4HC);
+    if (hc) ea.method_mask &= ~(1u << AMBC_M_LZ4);
+    if (deflate || dict || hc) {
+        // RLE / Huffman payloads wait for the later encoders' verdict (id 2, id 5, id 9 hc);
         // a second k_encode launch emits the ones they did not replace
         HIPCHK(d.pending.ensure((size_t)std::max<uint32_t>(M, 1)));
         ea.pending = d.pending.as<uint8_t>();
@@ -397,8 +402,13 @@ static int compress_on_body(Dev& d, const uint8_t* d_in, uint64_t n, const ambc_
         } else if (deflate) {
             HIPCHK(z9 ? launch_zlib9(e, s) : launch_deflate(e, s));
         }
-        if (deflate || dict) {
-            EncArgs ep = e;                 // RLE/Huffman payloads ids 2 / 5 did not replace
+        if (hc) {                           // id 9, the highest id, against the best of the others
+            EncArgs eh = e;
+            eh.method_mask |= 1u << AMBC_M_LZ4;
+            HIPCHK(launch_lz4hc(eh, ts));
+        }
+        if (deflate || dict || hc) {
+            EncArgs ep = e;                 // RLE/Huffman payloads ids 2 / 5 / 9 did not replace
             ep.flags |= ENC_EMIT_PENDING;
             ep.bestpre = nullptr;
             ep.stamps = nullptr;
@@ -810,7 +820,10 @@ static int run_encode_only(Dev& d, const uint8_t* h_in, uint64_t n, const ambc_p
     ea.su = su ? d.seg.as<uint8_t>() : nullptr;
     ea.flags = flags;
     for (int i = 0; i < 16; i++) { ea.pref_min[i] = p->pref_min[i]; ea.pref_max[i] = p->pref_max[i]; }
-    HIPCHK(launch_encode(ea, s));
+    // a forced id 9 with AMBC_FLAG_LZ4HC (ambc_encode_method_ex): k_lz4hc alone
+    const bool hc_only = (flags & ENC_FORCE) && (p->flags & AMBC_FLAG_LZ4HC) && p->method_mask == (1u << AMBC_M_LZ4);
+    if (hc_only) HIPCHK(launch_lz4hc(ea, s));
+    else HIPCHK(launch_encode(ea, s));
     // id 2: selection, and its should_use bit under ENC_ANALYZE
     if (((p->method_mask >> AMBC_M_DICT) & 1) || (flags & ENC_ANALYZE))
         HIPCHK(launch_dict(ea, std::min<uint32_t>(dict_cmax(p), 8192), s));
@@ -834,7 +847,16 @@ static int run_encode_only(Dev& d, const uint8_t* h_in, uint64_t n, const ambc_p
 
 extern "C" int ambc_encode_method(ambc_ctx* ctx, int method_id, const uint8_t* in, uint32_t n,
                                   uint8_t* out, uint32_t out_cap, uint32_t* out_len) {
+    return ambc_encode_method_ex(ctx, method_id, 0, in, n, out, out_cap, out_len);
+}
+
+extern "C" int ambc_encode_method_ex(ambc_ctx* ctx, int method_id, uint32_t flags, const uint8_t* in, uint32_t n,
+                                     uint8_t* out, uint32_t out_cap, uint32_t* out_len) {
     if (!ctx || ctx->devs.empty() || !out_len || (!in && n)) return fail(AMBC_E_INVAL, "NULL argument");
+    if (flags & ~AMBC_FLAG_LZ4HC) return fail(AMBC_E_INVAL, "ambc_encode_method_ex takes AMBC_FLAG_LZ4HC only");
+    const bool hc = method_id == AMBC_M_LZ4 && (flags & AMBC_FLAG_LZ4HC);
+    if (hc && n > LZ4HC_MAX_CHUNK)
+        return fail(AMBC_E_INVAL, "the GPU LZ4-HC encoder (AMBC_FLAG_LZ4HC) takes at most 16384 bytes");
     if (method_id != AMBC_M_RLE && method_id != AMBC_M_DICT && method_id != AMBC_M_HUFFMAN &&
         method_id != AMBC_M_LZ4 && method_id != AMBC_M_DELTA)
         return fail(AMBC_E_INVAL, "ambc_encode_method supports ids 1, 2, 3, 4 and 9");
@@ -848,6 +870,7 @@ extern "C" int ambc_encode_method(ambc_ctx* ctx, int method_id, const uint8_t* i
     for (int i = 0; i < 16; i++) { p.pref_min[i] = 0; p.pref_max[i] = 0xFFFFFFFFu; }
     std::vector<uint8_t> ids, slot;
     std::vector<uint32_t> plen;
+    if (hc) p.flags = AMBC_FLAG_LZ4HC;
     int rc = run_encode_only(ctx->devs[0], in, n, &p, ENC_FORCE, ids, plen, nullptr, &slot);
     if (rc) return rc;
     if (ids[0] != method_id) return fail(AMBC_E_CODEC, "codec raises on this input");

@@ -184,6 +184,9 @@ hipError_t launch_walk_check(const WalkArgs& a, hipStream_t s);
 hipError_t launch_encode(const EncArgs& a, hipStream_t s);
 hipError_t launch_deflate(const EncArgs& a, hipStream_t s);   // ambc_deflate.hip
 hipError_t launch_dict(const EncArgs& a, uint32_t cmax, hipStream_t s);   // ambc_dict.hip
+// id 9 as "ambc-lz4 hc v1" against the winner so far (ambc_lz4hc.hip): chunk_size <= LZ4HC_MAX_CHUNK,
+// method_mask with bit 9; ENC_FORCE: the chunk's frame whatever its size (stored if it would not shrink)
+hipError_t launch_lz4hc(const EncArgs& a, hipStream_t s);
 // DictionaryCompression(window, lookahead) for any window / lookahead / length
 // (ambc_dictany.hip): device scratch sized by the dict_any_* helpers
 struct DictAnyArgs {

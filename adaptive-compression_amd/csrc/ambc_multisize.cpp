@@ -157,6 +157,7 @@ extern "C" int ambc_compress_multisize_ex(ambc_ctx* ctx, const uint8_t* in, uint
     if (hc && (!hc->eval || !hc->emit)) hc = nullptr;
     if (!ctx || ctx->devs.empty() || !p || !out_len || (n && !in) || !cands_in || !n_cands_in)
         return fail(AMBC_E_INVAL, "bad arguments");
+    if (p->flags & AMBC_FLAG_LZ4HC) return fail(AMBC_E_INVAL, "LZ4HC is not available in the multi-size walk");
     for (uint32_t i = 0; i < n_cands_in; i++)
         if (cands_in[i] == 0 || cands_in[i] > (1u << 17)) return fail(AMBC_E_INVAL, "candidate sizes must be in [1, 131072]");
     const uint32_t allowed = (1u << AMBC_M_RLE) | (1u << AMBC_M_DICT) | (1u << AMBC_M_HUFFMAN) |

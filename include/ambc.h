@@ -61,6 +61,11 @@ extern "C" {
 #define AMBC_FLAG_INPUT_PADDED 4u /* device-resident calls: at least 64 readable bytes follow the
                                      input (chunks >= 4 KiB are then read in place instead of
                                      through an LDS copy; host-fed calls always qualify) */
+#define AMBC_FLAG_LZ4HC 8u        /* id 9 = "ambc-lz4 hc v1" (hash chains, one-step lazy parse:
+                                     ambc_lz4hc_model's bytes) instead of "ambc-lz4 greedy v2";
+                                     chunk_size <= 16384, id 9 gated by its prefs alone.  Not
+                                     available in the multi-size walk (ambc_compress_multisize*
+                                     return AMBC_E_INVAL with it) */
 
 /* GPU-routable method ids (bit i of method_mask = method id i) */
 #define AMBC_M_RLE 1
@@ -217,6 +222,10 @@ int ambc_compress_device(ambc_ctx* ctx, int dev, const void* d_in, uint64_t n,
  * (1<<1 RLE, 1<<2 Dictionary, 1<<3 Huffman, 1<<4 Delta) the selector evaluated. */
 int ambc_encode_method(ambc_ctx* ctx, int method_id, const uint8_t* in, uint32_t n, uint8_t* out,
                        uint32_t out_cap, uint32_t* out_len);
+/* ambc_encode_method with flags: AMBC_FLAG_LZ4HC and id 9 give the chunk's "ambc-lz4 hc v1"
+ * frame (n <= 16384, else AMBC_E_INVAL); flags = 0 is ambc_encode_method.  Other flags: AMBC_E_INVAL. */
+int ambc_encode_method_ex(ambc_ctx* ctx, int method_id, uint32_t flags, const uint8_t* in, uint32_t n,
+                          uint8_t* out, uint32_t out_cap, uint32_t* out_len);
 int ambc_analyze(ambc_ctx* ctx, const uint8_t* in, uint64_t n, const ambc_params* p, uint8_t* ids,
                  uint32_t* payload_len, uint8_t* should_use);
 /* DictionaryCompression(window_size, lookahead_size).compress(data) for any
@@ -349,6 +358,16 @@ int ambc_last_encode_launches(ambc_ctx* ctx, int dev, uint32_t* n_launch);
  * AMBC_E_MARKER where _adaptive_decompress would raise */
 int ambc_debug_walk(const uint8_t* body, uint64_t body_len, uint64_t orig_size, uint32_t threads,
                     uint64_t* n_pkgs, uint64_t* total, uint64_t* ns);
+
+/* "ambc-lz4 hc v1" (AMBC_FLAG_LZ4HC's id-9 encoder) as a serial model, host code
+ * only (no context, no device): the whole one-block LZ4 frame of in[0, n),
+ * n <= 65536 -- the bytes the GPU encoder writes for a chunk (it takes
+ * n <= 16384).  n = 0 gives an empty output; AMBC_E_CAPACITY with *out_len = the
+ * frame's size when out_cap is short.  ambc_lz4hc_model_ex: the same parse with
+ * other constants (hash bits in [8, 16], chain depth >= 1), for measurements. */
+int ambc_lz4hc_model(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t out_cap, uint32_t* out_len);
+int ambc_lz4hc_model_ex(const uint8_t* in, uint32_t n, uint32_t hash_bits, uint32_t depth, uint8_t* out,
+                        uint32_t out_cap, uint32_t* out_len);
 
 /* test hook, never set by the library itself: the sharded compress of rank
  * `rank` fails right after its pre-flight (-1, the default: no injection) --
